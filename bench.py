@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): images/sec of the DensePose hot path on R_50_FPN_s1x, 800x1333 frames,
 batch 8 per GPU, bf16 operands / fp32 accumulate, detections pinned to R = 8 per image.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one rank per GPU. Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a rank; run
 bare (`python bench.py --gpus 8`) it starts the N ranks itself as child processes - before anything here touches the
@@ -34,6 +34,33 @@ def make_frames(n, start, hw, device):
     h, w = hw
     return [torch.from_numpy(np.random.default_rng(1234 + start + i).integers(0, 256, (h, w, 3), dtype=np.uint8)).to(device)
             for i in range(n)]
+
+
+DUMP_BUDGET_BYTES = 60 << 20   # --dump-outputs writes at most this much array data (the limit is 64 MB with the .npy headers)
+
+
+def dump_outputs(out, directory, budget_bytes=DUMP_BUDGET_BYTES):
+    """--dump-outputs DIR: the results one timed step returned to its caller, one `frame<i>_<key>.npy` per frame and key.
+    Floating outputs are written as float32, integer ones as float64 (exact). When the whole would exceed `budget_bytes`,
+    every array of more than 2**16 elements (the IUV maps) is replaced by the same fraction of its elements, taken in
+    ascending flat-index order at the positions np.random.default_rng(0).choice(size, count, replace=False) selects: the
+    sample depends only on the array's shape, so two builds that return equal shapes are compared element for element."""
+    arrays = {}
+    for i, res in enumerate(out):
+        for k, v in res.items():
+            a = v.detach().cpu()
+            a = a.double() if not a.is_floating_point() else a.float()
+            arrays["frame%d_%s" % (i, k)] = a.numpy()
+    big = {k for k, a in arrays.items() if a.size > 1 << 16}
+    small_bytes = sum(a.nbytes for k, a in arrays.items() if k not in big)
+    big_bytes = sum(arrays[k].nbytes for k in big)
+    frac = 1.0 if small_bytes + big_bytes <= budget_bytes else max(0.0, budget_bytes - small_bytes) / big_bytes
+    os.makedirs(directory, exist_ok=True)
+    for k, a in arrays.items():
+        if k in big and frac < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, k + ".npy"), a)
 
 
 def cpu_baseline(cfg, state, hw, budget_s):
@@ -263,8 +290,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=25.0)
     ap.add_argument("--no-extras", action="store_true", help="skip the accuracy / R-sensitivity / single-frame latency extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0's frames; see dump_outputs; "
+                         "bench_outputs/ is git-ignored)")
     ap.add_argument("--spawn-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ---- self-launch: `python bench.py --gpus N` without a launcher starts its own N ranks (fresh child processes, started
     # before this process has made any GPU call; a process that initialised the GPU is never re-executed)
@@ -357,6 +389,8 @@ def main():
     pred.join()
     barrier()
     elapsed = time.perf_counter() - t_begin
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)   # before any later step reuses the buffers the last timed step returned
     # the same loop held for >= 3 s (the K-step region above is ~0.1 s at the default K: too short to say anything about the
     # clock the chip sustains) and, beside it, the same workload with the frames starting in PAGEABLE HOST memory like the
     # reference's run.py:34-36 hands them over (pinned ring + one H2D per batch on a copy stream, predictor._HostFrameRing)

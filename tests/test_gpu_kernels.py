@@ -935,10 +935,11 @@ def test_conv3x3_rows_kernel(eng, dt, case, variant, policy):
     e = eng[dt]
     Ci, Co, N, H, W, live, relu = case
     two_ok = (Ci == 512 and _rows2_width_ok(W)) or (Ci == 256 and _rows2_width_ok(W, 1 << 30))
+    # the 32-pixel form takes 512 input channels and widths with strip groups of at most 8 images: on any other shape the rows2
+    # variants must fall back to the 16-pixel form (class 7) and give its results
+    two = variant.startswith("rows2") and two_ok
     policy.default("conv_rows2_lockstep")
     if variant.startswith("rows2"):
-        if not two_ok:
-            pytest.skip("the 32-pixel form takes 512 input channels and widths with strip groups of at most 8 images")
         policy.default("conv_rows2")
         policy.set("conv_rows2_256", "1")     # every 256-channel layer (default: only those the weight-stationary kernel does not take)
         if variant == "rows2_lockstep":
@@ -957,21 +958,21 @@ def test_conv3x3_rows_kernel(eng, dt, case, variant, policy):
     p.stride, p.ntaps, p.dtype, p.hi_off, p.wi_off = 1, 9, e.dt, -1, -1
     p.osN, p.osH, p.osW = H * W * Co, W * Co, Co
     p.out = 4096
-    assert e.lib.dp_conv2d_kernel_class(C.byref(p)) == (8 if variant.startswith("rows2") else 7)
+    assert e.lib.dp_conv2d_kernel_class(C.byref(p)) == (8 if two else 7)
     n_dev = None if live is None else torch.tensor([live], dtype=torch.int32, device=e.device)
     # the default policy: a call site is on this kernel class for every batch or for none - 512-channel layers whose width suits the
     # 32-pixel form always (the DensePose head's ROI maps, sized on the device or not), other 512-channel layers on plain tensors
     # (res5's conv2) on the 16-pixel form; the 256 -> 512 layer and device-sized launches of other widths are not
     policy.default("conv_rows")
     p.n_dev = None if n_dev is None else n_dev.data_ptr()
-    if variant.startswith("rows2"):
+    if two:
         assert e.lib.dp_conv2d_kernel_class(C.byref(p)) == 8
         # 256 input channels: by default only the layers with another cout count (the head's 256 -> 512 first layer)
         policy.default("conv_rows2_256")
         assert (e.lib.dp_conv2d_kernel_class(C.byref(p)) == 8) == (Ci == 512 or Co != 256)
         policy.set("conv_rows2_256", "1")
     else:
-        assert (e.lib.dp_conv2d_kernel_class(C.byref(p)) == 7) == (Ci == 512 and live is None)     # (DP_CONV_ROWS2=0 in this variant)
+        assert (e.lib.dp_conv2d_kernel_class(C.byref(p)) == 7) == (Ci == 512 and live is None)     # (no 32-pixel form: policy or shape)
     p.n_dev = None
     policy.set("conv_rows", "2")
     nl = N if live is None else live
