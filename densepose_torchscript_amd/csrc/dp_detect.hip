@@ -657,6 +657,21 @@ struct RoiArgs {
   int items_per_block;
 };
 
+// poolers.py:43-51: level = clamp(floor(4 + log2(sqrt(area) / 224 + 1e-8)), min_level, max_level) - min_level, every step in fp32
+// like the reference's CPU ops. The log2 must be the CORRECTLY ROUNDED fp32 one: the fp32 pipeline decides between two levels a few
+// ulps below a power of two, and there device log2f is not correctly rounded - boxes whose sqrt(area) lay a few ulps from 112 / 56 were
+// pooled from the neighbouring level (tests/test_gpu_detect.py). The double log2 of the fp32 argument, rounded to fp32, is correctly
+// rounded there (tests/test_oracle_ops.py checks its distance from every rounding midpoint near the boundaries).
+__device__ __forceinline__ int roi_level(float bx1, float by1, float bx2, float by2, int min_level, int n_levels) {
+  const float area = (bx2 - bx1) * (by2 - by1);
+  const float sz = sqrtf(area);
+  const float lg = (float)log2((double)(sz / 224.0f + 1e-8f));
+  float lv = floorf(4.0f + lg);
+  const float lo = (float)min_level, hi = (float)(min_level + n_levels - 1);
+  lv = fminf(fmaxf(lv, lo), hi);   // NaN (negative area) -> fmaxf returns lo, torch.clamp would give NaN->int; never happens (w,h >= 0)
+  return (int)lv - min_level;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void roi_align_kernel(const RoiArgs p) {
   const int img = blockIdx.z, j = blockIdx.y;
@@ -675,16 +690,7 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const RoiArgs p) {
   }
   const float* b = p.boxes + ((long long)img * p.max_rois + j) * 4;
   const float bx1 = b[0], by1 = b[1], bx2 = b[2], by2 = b[3];
-  int lvl = 0;
-  if (p.n_levels > 1) {
-    // poolers.py:43-51
-    const float area = (bx2 - bx1) * (by2 - by1);
-    const float sz = sqrtf(area);
-    float lv = floorf(4.0f + log2f(sz / 224.0f + 1e-8f));
-    const float lo = (float)p.min_level, hi = (float)(p.min_level + p.n_levels - 1);
-    lv = fminf(fmaxf(lv, lo), hi);   // NaN (negative area) -> fmaxf returns lo, torch.clamp would give NaN->int; never happens (w,h >= 0)
-    lvl = (int)lv - p.min_level;
-  }
+  const int lvl = p.n_levels > 1 ? roi_level(bx1, by1, bx2, by2, p.min_level, p.n_levels) : 0;
   const int H = p.Hl[lvl], W = p.Wl[lvl], C = p.C, P = p.P, g = p.sampling;
   const float scale = p.scale[lvl];
   const T* __restrict__ feat = reinterpret_cast<const T*>(p.feat[lvl]) + (long long)img * H * W * C;
@@ -783,15 +789,7 @@ __global__ __launch_bounds__(256) void roi_align_tab_kernel(const RoiArgs p) {
   __shared__ int t_in[2][kRoiTab];
   const float* b = p.boxes + ((long long)img * p.max_rois + j) * 4;
   const float bx1 = b[0], by1 = b[1], bx2 = b[2], by2 = b[3];
-  int lvl = 0;
-  if (p.n_levels > 1) {
-    const float area = (bx2 - bx1) * (by2 - by1);
-    const float sz = sqrtf(area);
-    float lv = floorf(4.0f + log2f(sz / 224.0f + 1e-8f));
-    const float lo = (float)p.min_level, hi = (float)(p.min_level + p.n_levels - 1);
-    lv = fminf(fmaxf(lv, lo), hi);
-    lvl = (int)lv - p.min_level;
-  }
+  const int lvl = p.n_levels > 1 ? roi_level(bx1, by1, bx2, by2, p.min_level, p.n_levels) : 0;
   const int H = p.Hl[lvl], W = p.Wl[lvl];
   const float scale = p.scale[lvl];
   const T* __restrict__ feat = reinterpret_cast<const T*>(p.feat[lvl]) + (long long)img * H * W * C;

@@ -10,10 +10,10 @@
 #include <stdlib.h>
 #include <string.h>
 
-/* input [N][C][H][W], rois [K][5] = (batch, x1, y1, x2, y2), out [K][C][P][P] */
-void oracle_roi_align_f32(const float* input, int N, int C, int H, int W, const float* rois, int K, int P, float spatial_scale,
-                          int sampling, int aligned, float* out) {
-  (void)N;
+/* input [N][C][H][W], rois [K][5] = (batch, x1, y1, x2, y2), out [K][C][P][P]: out32 (fp32 sums, torchvision's arithmetic) or
+ * out64 (the same fp32 sample geometry - positions, corners, fp32 weights hy, hx, ly, lx - with the products and sums in double) */
+static void roi_align_impl(const float* input, int C, int H, int W, const float* rois, int K, int P, float spatial_scale,
+                           int sampling, int aligned, float* out32, double* out64) {
 #pragma omp parallel for schedule(dynamic, 4)
   for (int k = 0; k < K; ++k) {
     const float* r = rois + (size_t)k * 5;
@@ -54,25 +54,46 @@ void oracle_roi_align_f32(const float* input, int N, int C, int H, int W, const 
       }
     for (int c = 0; c < C; ++c) {
       const float* f = input + ((size_t)b * C + c) * H * W;
-      float* o = out + ((size_t)k * C + c) * P * P;
+      const size_t o = ((size_t)k * C + c) * P * P;
       for (int ph = 0; ph < P; ++ph)
         for (int pw = 0; pw < P; ++pw) {
           float acc = 0.0f;
+          double acc64 = 0.0;
           for (int iy = 0; iy < g; ++iy) {
             const int sy = ph * g + iy;
             for (int ix = 0; ix < g; ++ix) {
               const int sx = pw * g + ix;
               if (bad[sy] || bad[ns + sx]) continue;
-              const float w1 = hyv[sy] * hxv[sx], w2 = hyv[sy] * wx[sx], w3 = wy[sy] * hxv[sx], w4 = wy[sy] * wx[sx];
-              acc += w1 * f[ylo[sy] * W + xlo[sx]] + w2 * f[ylo[sy] * W + xhi[sx]] + w3 * f[yhi[sy] * W + xlo[sx]] +
-                     w4 * f[yhi[sy] * W + xhi[sx]];
+              const float f1 = f[ylo[sy] * W + xlo[sx]], f2 = f[ylo[sy] * W + xhi[sx]];
+              const float f3 = f[yhi[sy] * W + xlo[sx]], f4 = f[yhi[sy] * W + xhi[sx]];
+              if (out64) {
+                const double w1 = (double)hyv[sy] * hxv[sx], w2 = (double)hyv[sy] * wx[sx];
+                const double w3 = (double)wy[sy] * hxv[sx], w4 = (double)wy[sy] * wx[sx];
+                acc64 += w1 * f1 + w2 * f2 + w3 * f3 + w4 * f4;
+              } else {
+                const float w1 = hyv[sy] * hxv[sx], w2 = hyv[sy] * wx[sx], w3 = wy[sy] * hxv[sx], w4 = wy[sy] * wx[sx];
+                acc += w1 * f1 + w2 * f2 + w3 * f3 + w4 * f4;
+              }
             }
           }
-          o[ph * P + pw] = acc / count;
+          if (out64) out64[o + ph * P + pw] = acc64 / count;
+          else out32[o + ph * P + pw] = acc / count;
         }
     }
     free(ylo); free(wy); free(bad);
   }
+}
+
+void oracle_roi_align_f32(const float* input, int N, int C, int H, int W, const float* rois, int K, int P, float spatial_scale,
+                          int sampling, int aligned, float* out) {
+  (void)N;
+  roi_align_impl(input, C, H, W, rois, K, P, spatial_scale, sampling, aligned, out, NULL);
+}
+
+void oracle_roi_align_f64acc(const float* input, int N, int C, int H, int W, const float* rois, int K, int P, float spatial_scale,
+                             int sampling, int aligned, double* out) {
+  (void)N;
+  roi_align_impl(input, C, H, W, rois, K, P, spatial_scale, sampling, aligned, NULL, out);
 }
 
 /* boxes [n][4], order [n] = indices sorted by score descending (stable); keep_out [n]; returns number kept */

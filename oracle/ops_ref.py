@@ -42,7 +42,10 @@ if os.path.exists(_so) and os.environ.get("ORACLE_NO_C", "0") != "1":
         _C = None
 
 
-def roi_align(input, rois, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False, backend=None):
+def roi_align(input, rois, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False, backend=None, acc_dtype=None):
+    """acc_dtype=torch.float64 (fp32 input only): the same fp32 sample geometry, the bilinear products and sums in double - the
+    high-precision restatement the HIP kernels' fp32 sums are measured against."""
+    assert acc_dtype in (None, torch.float64) and (acc_dtype is None or input.dtype == torch.float32)
     use_c = (_C is not None) if backend is None else (backend == "c")
     if use_c and input.dtype == torch.float32 and rois.shape[0] > 0:
         if isinstance(output_size, (tuple, list)):
@@ -52,11 +55,12 @@ def roi_align(input, rois, output_size, spatial_scale=1.0, sampling_ratio=-1, al
         r = rois.to(torch.float32).contiguous()
         N, Cc, H, W = x.shape
         K = r.shape[0]
-        out = torch.empty((K, Cc, int(output_size), int(output_size)), dtype=torch.float32)
-        _C.oracle_roi_align_f32(ctypes.c_void_p(x.data_ptr()), N, Cc, H, W, ctypes.c_void_p(r.data_ptr()), K, int(output_size),
-                                ctypes.c_float(spatial_scale), int(sampling_ratio), int(bool(aligned)), ctypes.c_void_p(out.data_ptr()))
+        out = torch.empty((K, Cc, int(output_size), int(output_size)), dtype=acc_dtype or torch.float32)
+        fn = _C.oracle_roi_align_f32 if acc_dtype is None else _C.oracle_roi_align_f64acc
+        fn(ctypes.c_void_p(x.data_ptr()), N, Cc, H, W, ctypes.c_void_p(r.data_ptr()), K, int(output_size),
+           ctypes.c_float(spatial_scale), int(sampling_ratio), int(bool(aligned)), ctypes.c_void_p(out.data_ptr()))
         return out
-    return _roi_align_torch(input, rois, output_size, spatial_scale, sampling_ratio, aligned)
+    return _roi_align_torch(input, rois, output_size, spatial_scale, sampling_ratio, aligned, acc_dtype)
 
 
 def nms_threshold_f32(iou_threshold):
@@ -82,15 +86,17 @@ def nms(boxes, scores, iou_threshold, backend=None):
     return _nms_numpy(boxes, scores, iou_threshold)
 
 
-def _roi_align_torch(input, rois, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False):
-    """input [N,C,H,W] float, rois [K,5] (batch, x1, y1, x2, y2) -> [K,C,ph,pw]."""
+def _roi_align_torch(input, rois, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False, acc_dtype=None):
+    """input [N,C,H,W] float, rois [K,5] (batch, x1, y1, x2, y2) -> [K,C,ph,pw]. Geometry in the input's dtype, the weighted sums
+    in acc_dtype (default: the input's)."""
     if isinstance(output_size, int):
         output_size = (output_size, output_size)
     ph, pw = int(output_size[0]), int(output_size[1])
     N, C, H, W = input.shape
     K = rois.shape[0]
     dt = input.dtype
-    out = torch.zeros((K, C, ph, pw), dtype=dt)
+    at = acc_dtype or dt
+    out = torch.zeros((K, C, ph, pw), dtype=at)
     if K == 0:
         return out
     assert sampling_ratio > 0, "hot path always uses sampling_ratio=2"
@@ -134,12 +140,13 @@ def _roi_align_torch(input, rois, output_size, spatial_scale=1.0, sampling_ratio
 
     inv_y, ylo, yhi, ly, hy = prep(yy, H)
     inv_x, xlo, xhi, lx, hx = prep(xx, W)
+    ly, hy, lx, hx = (t.to(at) for t in (ly, hy, lx, hx))
     count = float(max(g * g, 1))
     # process per ROI chunk to bound memory
     for k0 in range(0, K, 64):
         k1 = min(K, k0 + 64)
         kk = k1 - k0
-        feat = input[bidx[k0:k1]]  # [kk,C,H,W]
+        feat = input[bidx[k0:k1]].to(at)  # [kk,C,H,W]
         Yl = ylo[k0:k1][:, :, None].expand(kk, ph * g, pw * g)
         Yh = yhi[k0:k1][:, :, None].expand(kk, ph * g, pw * g)
         Xl = xlo[k0:k1][:, None, :].expand(kk, ph * g, pw * g)
@@ -156,10 +163,10 @@ def _roi_align_torch(input, rois, output_size, spatial_scale=1.0, sampling_ratio
         w4 = (ly[k0:k1][:, :, None] * lx[k0:k1][:, None, :])[:, None]
         val = w1 * gather(Yl, Xl) + w2 * gather(Yl, Xh) + w3 * gather(Yh, Xl) + w4 * gather(Yh, Xh)
         invalid = (inv_y[k0:k1][:, :, None] | inv_x[k0:k1][:, None, :])[:, None]
-        val = torch.where(invalid, torch.zeros((), dtype=dt), val)
+        val = torch.where(invalid, torch.zeros((), dtype=at), val)
         # accumulate the g x g samples of each bin in (iy, ix) order like the kernel does
         val = val.reshape(kk, C, ph, g, pw, g)
-        acc = torch.zeros((kk, C, ph, pw), dtype=dt)
+        acc = torch.zeros((kk, C, ph, pw), dtype=at)
         for a in range(g):
             for b in range(g):
                 acc = acc + val[:, :, :, a, :, b]

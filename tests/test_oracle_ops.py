@@ -229,6 +229,55 @@ def test_c_backend_equals_numpy_backend_bit_for_bit():
         assert torch.equal(ops_ref.nms(boxes, scores, thr, backend="c"), ops_ref.nms(boxes, scores, thr, backend="numpy"))
 
 
+def test_roi_level_log2_is_correctly_rounded_where_the_level_is_decided():
+    """The ROIPooler level floor(4 + log2(u)) (poolers.py:43-51, u = sqrt(area) / 224 + 1e-8, all fp32) only depends on how log2 rounds
+    for u a few ulps from a power of two. There, for every fp32 u within 600 ulps of 2^-4 .. 2^3: the reference's fp32 torch.log2 is the
+    correctly rounded log2 (60-digit mpmath), and the exact value is far enough from every fp32 rounding midpoint (> 2^-40 relative)
+    that a double log2 within a few double ulps - what dp_detect.hip's roi_level rounds to fp32 - gives that float too."""
+    import mpmath
+    mpmath.mp.dps = 60
+    us = []
+    for m in range(-4, 4):
+        b = np.array([2.0 ** m], np.float32).view(np.int32)[0]
+        us.append((b + np.arange(-600, 601, dtype=np.int32)).view(np.float32))
+    u = np.concatenate(us)
+    got_torch = torch.log2(torch.from_numpy(u)).numpy()
+    got_double = np.log2(u.astype(np.float64)).astype(np.float32)
+    four = np.float32(4)
+    for x, t, d in zip(u.tolist(), got_torch.tolist(), got_double.tolist()):
+        exact = mpmath.log(mpmath.mpf(x), 2)
+        cr = np.float32(float(exact))                    # double rounding is harmless given the margin asserted below
+        assert d == cr, (x, d, cr)
+        # torch's log2 is not correctly rounded everywhere (1 ulp off ~600 ulps below 1.0), but the level it gives is
+        assert np.floor(four + np.float32(t)) == np.floor(four + cr), (x, t, cr)
+        if exact == 0:
+            continue
+        lo = np.nextafter(cr, np.float32(-np.inf))
+        hi = np.nextafter(cr, np.float32(np.inf))
+        for mid in ((mpmath.mpf(float(lo)) + mpmath.mpf(float(cr))) / 2, (mpmath.mpf(float(hi)) + mpmath.mpf(float(cr))) / 2):
+            assert abs(exact - mid) > abs(exact) * mpmath.mpf(2) ** -40, x
+
+
+def test_roi_align_double_accumulation_backends_agree_and_keep_the_fp32_geometry():
+    """acc_dtype=float64 (the reference the GPU ROIAlign tests measure against): the C and torch restatements agree bit for bit,
+    and they differ from the fp32 oracle only by the fp32 rounding of the sums - the sample geometry is the same."""
+    import pytest
+    if ops_ref._C is None:
+        pytest.skip("oracle/_ops_c.so not built")
+    rng = np.random.default_rng(4)
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn((2, 16, 30, 44), generator=g)
+    xy = rng.uniform(-20, 150, (120, 2)).astype(np.float32)
+    wh = rng.uniform(0, 90, (120, 2)).astype(np.float32)
+    rois = torch.from_numpy(np.concatenate([rng.integers(0, 2, (120, 1)).astype(np.float32), xy, xy + wh], 1))
+    for P, sc in ((7, 0.25), (14, 0.125), (3, 1.0)):
+        a = ops_ref.roi_align(x, rois, P, sc, 2, False, backend="c", acc_dtype=torch.float64)
+        b = ops_ref.roi_align(x, rois, P, sc, 2, False, backend="torch", acc_dtype=torch.float64)
+        assert a.dtype == torch.float64 and torch.equal(a, b)
+        f32 = ops_ref.roi_align(x, rois, P, sc, 2, False, backend="c")
+        assert float((f32.double() - a).abs().max()) <= 16 * 2.0 ** -24 * float(x.abs().max())
+
+
 def test_bilinear_restatement_is_bit_exact():
     """The arithmetic dp_iuv_extract implements for the visualiser's F.interpolate(bilinear, align_corners=False)
     (visualizer.py:14-16,24-25): src = fma(scale, dst + 0.5, -0.5), value = fma(wy0, fma(wx0, a, wx1*b), wy1 * fma(wx0, c, wx1*d)).
